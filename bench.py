@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the VideoPose3D temporal-model hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 Workload (BASELINE.json `metric`: "frames/sec (fwd+bwd) 243-frame arc=3,3,3,3,3 B=1024"):
   one step = one training pass (forward + backward incl. BatchNorm statistics and dropout p=0.25) of
@@ -777,6 +777,24 @@ def shape_sweep(dev, steps=20):
                     "(%.0f GFLOP of forward work) selects" % (keep[True] / 1e9), "rows": rows}
 
 
+DUMP_MAX_ELEMS = 1 << 20
+
+
+def dump_outputs(out_dir, loss, pred, model):
+    """--dump-outputs: what the caller of the timed step receives from its last execution, as float32 .npy files (loss, predicted
+    poses, every parameter's gradient).  A gradient above DUMP_MAX_ELEMS elements is written as the same seeded sample of its
+    flattened values in every run (at most ~40 MB in all for the benchmark model), so that two builds compare file for file."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss, "pred": pred}
+    arrays.update(("grad." + n, p.grad) for n, p in model.named_parameters())
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def relaunch_under_torchrun(n_gpus):
     """`python bench.py --gpus N` without an external launcher: start N ranks of this script through
     torch.distributed.run on one node (rendezvous on 127.0.0.1, a free port) and hand back its exit code; rank 0 of the
@@ -848,7 +866,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--windows", type=int, default=5, help="timed windows of --steps steps each; `value` is the median window")
+    ap.add_argument("--windows", type=int, default=1, help="timed windows of --steps steps each (default: one, so that --steps is "
+                    "the number of timed steps); `value` is the median window")
     ap.add_argument("--no-settle", action="store_true", help="skip the untimed settle phase before the warm-up")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-eval", action="store_true", help="skip the cfg2 eval-forward section")
@@ -857,6 +876,9 @@ def main():
     ap.add_argument("--no-rocm-ref", action="store_true", help="skip the PyTorch-ROCm (MIOpen) reference-path baseline (~75 s)")
     ap.add_argument("--no-sweep", action="store_true", help="skip the shape sweep (run.py's default arc 3,3,3 / 3,3,3,3 on both engines)")
     ap.add_argument("--dry-run", action="store_true", help="launcher / barrier control flow only, no GPU work (CPU test hook)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, predicted poses, parameter gradients; "
+                         "a fixed seeded sample of each gradient above %d elements) to DIR/<name>.npy" % DUMP_MAX_ELEMS)
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(relaunch_under_torchrun(args.gpus))       # bare `python bench.py --gpus N`: one rank per GPU, ourselves
@@ -895,11 +917,14 @@ def main():
 
         def step():
             sync.zero_grad()
-            loss = vloss.mpjpe(model(x), tgt)           # loss.py:11-17 on the HIP path (one kernel: value + gradient)
+            pred = model(x)
+            loss = vloss.mpjpe(pred, tgt)               # loss.py:11-17 on the HIP path (one kernel: value + gradient)
             loss.backward()
             sync.sync()
+            last["pred"], last["loss"] = pred.detach(), loss.detach()
             return loss
         return model, sync, step
+    last = {}
 
     def one_window(step, steps, events=True):
         """EXACTLY `steps` steps between two fences (barrier + device sync on both sides), max over ranks.  Also returned:
@@ -940,10 +965,12 @@ def main():
         # every rank must leave after the same number of windows (the windows hold collectives): dt is already the max over ranks
         return ms
 
-    def time_steps(step, warmup, steps, windows=1, do_settle=False, detail=None):
+    def time_steps(step, warmup, steps, windows=1, do_settle=False, detail=None, model=None):
         """W untimed warm-up steps, then `windows` timed windows of EXACTLY `steps` steps each; the reported time is the
         MEDIAN window (all windows are listed in `detail`)."""
         settle_ms = settle(step, steps) if do_settle else []
+        if model is not None:
+            model._drop_calls = 0          # the dropout masks of warm-up and timed steps do not depend on how long settle ran
         for _ in range(warmup):
             step()
         res = [one_window(step, steps, events=detail is not None) for _ in range(windows)]
@@ -960,7 +987,10 @@ def main():
     n_windows = max(1, args.windows)
     model, sync, step = build(math)
     timing = {}
-    dt = time_steps(step, args.warmup, args.steps, windows=n_windows, do_settle=not args.no_settle, detail=timing)
+    dt = time_steps(step, args.warmup, args.steps, windows=n_windows, do_settle=not args.no_settle, detail=timing, model=model)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["loss"], last["pred"], model)
+    last.clear()
     ms_per_step = dt / args.steps * 1e3
     value = world * B * args.steps / dt
     dtype = "f16x3 (split-fp16 operands, fp32 accumulate)" if math == "f16x3" else "f32"

@@ -119,3 +119,31 @@ def test_box_state_reads_a_sysfs_tree_and_never_raises(tmp_path):
     assert "error" in bench.box_state(lambda: None, n_steps=1, samples=1, sysfs=str(tmp_path / "nothing"))
     line = json.loads(bench.final_line({"metric": "m", "box": out, "config": {}}))
     assert line["box"] == {"power_w": 1000.2, "power_cap_w": 1400.0, "sclk_mhz": 2226.9, "temp_junction_c": None}
+
+
+def test_dump_outputs_writes_every_output_within_the_budget(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): loss, predictions and one file per parameter gradient, float32; a gradient above
+    DUMP_MAX_ELEMS elements becomes the same seeded sample in every call, so that two runs compare file for file."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+    model = torch.nn.Sequential(torch.nn.Linear(8, 4), torch.nn.Linear(4, 4))
+    big = torch.nn.Parameter(torch.arange(bench.DUMP_MAX_ELEMS + 10, dtype=torch.float32))
+    model.register_parameter("big", big)
+    pred = model(torch.ones(2, 8))
+    loss = pred.sum() + (big * big).sum()
+    loss.backward()
+    bench.dump_outputs(str(tmp_path / "a"), loss, pred, model)
+    bench.dump_outputs(str(tmp_path / "b"), loss, pred, model)
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(["loss.npy", "pred.npy"] + ["grad.%s.npy" % n for n, _ in model.named_parameters()])
+    total = 0
+    for n in names:
+        a, b = np.load(str(tmp_path / "a" / n)), np.load(str(tmp_path / "b" / n))
+        assert a.dtype == np.float32 and np.array_equal(a, b), n
+        total += a.nbytes
+    assert np.array_equal(np.load(str(tmp_path / "a" / "pred.npy")), pred.detach().numpy())
+    g = np.load(str(tmp_path / "a" / "grad.big.npy"))
+    assert g.shape == (bench.DUMP_MAX_ELEMS,) and np.all(np.diff(g) > 0) and np.all(g % 2 == 0)    # distinct sorted 2*i
+    assert total <= 64 << 20

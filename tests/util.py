@@ -80,13 +80,16 @@ def gen_case_meta(z, name):
                 cams=bool(cams), num_batches=nb, num_frames=nf, n=int(z[name + "/n"]))
 
 
-def s16_or_skip(mode, model, t_in, training, need_dx=False):
-    """Under the f16x3 id a configuration the split-fp16 engine does not implement is skipped, not silently re-run on
-    the fp32 kernels (it is covered under the f32 id)."""
-    import pytest
+# set by s16_or_fallback, read by the math_mode fixture (tests/conftest.py): this f16x3 run must reach the fp32 engine
+EXPECT_F32_ONLY = {"on": False}
+
+
+def s16_or_fallback(mode, model, t_in, training, need_dx=False):
+    """Under the f16x3 id a configuration the split-fp16 engine does not implement runs on the fp32 kernels, as the library
+    runs it under math "f16x3"; the math_mode fixture then certifies that the fp32 engine served it."""
     from videopose3d_amd import engine
     if mode == "f16x3" and not engine.use_s16(model, t_in, training, need_dx):
-        pytest.skip("engine_s16.supported() rejects this configuration: covered under the f32 id")
+        EXPECT_F32_ONLY["on"] = True
 
 
 def unpack_act_bits(bits, m_rows, c):

@@ -162,6 +162,9 @@ def _forward_train_f32(mod, x3: torch.Tensor, save: bool, frozen: bool = False):
 
 
 _side_streams = {}
+# graph.GraphedStep: while set, a step runs on the caller's stream alone.  ONE graph captured across two streams replays its
+# branches serially on this runtime (no overlap to gain), and replaying such a graph segfaulted the host process (ROCm 7.0)
+_one_stream = False
 
 
 def _wgrad_stream(device, default_on: bool = False) -> Optional[torch.cuda.Stream]:
@@ -170,7 +173,7 @@ def _wgrad_stream(device, default_on: bool = False) -> Optional[torch.cuda.Strea
     dgrad is neutral (10.39 vs 10.34 ms/step: two fp32-MFMA GEMMs just split the matrix pipes), forking it under the
     next layer's HBM-bound BN-backward kernels costs 1.3 % (10.47 ms) -- the streaming kernels and the GEMM's
     L2-miss traffic contend for the fabric -- so the serial order stays the default."""
-    if os.environ.get("VP3D_OVERLAP", "1" if default_on else "0") != "1" or ops._prof is not None:
+    if os.environ.get("VP3D_OVERLAP", "1" if default_on else "0") != "1" or ops._prof is not None or _one_stream:
         return None
     key = torch.device(device).index
     st = _side_streams.get(key)

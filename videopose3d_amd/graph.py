@@ -361,32 +361,28 @@ class GraphedStep:
         counters = [(m._drop_calls, m._stats_epoch, m._drop_counter.clone()) for m in self.models]
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(self.warmup):              # lazily built helpers, code objects, allocator sizes, autograd buffers
-                for p in self._params():
-                    p.grad = None
-                self._run(e.x)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        with torch.no_grad():
-            for m, st, cn in zip(self.models, state, counters):
-                for b_, s_ in zip(m.buffers(), st):
-                    b_.copy_(s_)
-                m._drop_counter.copy_(cn[2])
-                m._drop_calls, m._stats_epoch = cn[0], cn[1]
-        for p in self._params():
-            p.grad = None
-        key = dev.index
-        cached = engine._side_streams.get(key)
-        engine._side_streams[key] = torch.cuda.Stream(device=dev)      # (a fresh second stream: see GraphedTrainStep._capture)
-        e.graph = _new_graph()
+        engine._one_stream = True                     # warm-up and capture: no second stream inside the one graph (engine.py)
         try:
+            with torch.cuda.stream(side):
+                for _ in range(self.warmup):          # lazily built helpers, code objects, allocator sizes, autograd buffers
+                    for p in self._params():
+                        p.grad = None
+                    self._run(e.x)
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            with torch.no_grad():
+                for m, st, cn in zip(self.models, state, counters):
+                    for b_, s_ in zip(m.buffers(), st):
+                        b_.copy_(s_)
+                    m._drop_counter.copy_(cn[2])
+                    m._drop_calls, m._stats_epoch = cn[0], cn[1]
+            for p in self._params():
+                p.grad = None
+            e.graph = _new_graph()
             with torch.cuda.graph(e.graph, capture_error_mode="thread_local"):
                 e.loss = self._run(e.x)
         finally:
-            e.keep = engine._side_streams.pop(key)
-            if cached is not None:
-                engine._side_streams[key] = cached
+            engine._one_stream = False
         _dump_dot(e.graph)
         for m, cn in zip(self.models, counters):
             m._drop_calls, m._stats_epoch = cn[0], cn[1]
